@@ -17,15 +17,30 @@ collective on the data path.  `python bench.py --gpus N` launches the N ranks it
 torch.distributed.run launch is used as is.  With N > 1 a strong-scaling
 figure (the 10M-row chunk split N ways) is reported beside it.
 
-Timing: W untimed warmup steps, then R = --repeats timed regions of exactly
-K steps, each bracketed by barrier + device sync on both sides; per region
-the max over ranks; `value` comes from the median region.
+Timing: W untimed warmup steps, then one timed region of exactly K = --steps
+steps, bracketed by barrier + device sync on both sides; the max over ranks;
+`value` and `ms_per_step` come from that region.  Set-up ends with SETTLE_S
+seconds of untimed decode steps, so the region starts at running clocks (it
+is the only one: there is no median over later regions).  A plain run does nothing
+else: set up, warm up, time the K steps, write the outputs (--dump-outputs)
+and print the result line.
 
-Further legs (not `value`): C3 regex page filter (configs[2]) and PLAIN
-decode, C4 8 mixed columns, C5 dictionary decode + regex, end-to-end (host
-walk + H2D + decode), CPU baselines.  Every leg's result is checked against
-the generator's own value dump (pinned to the oracle by the CPU tests) or the
-committed regex page-set digests (tests/golden/bench_expect.json).
+--dump-outputs DIR: after the timed steps, what the last timed step left in
+the decoded column (validity, offsets, chars: what a caller of the decode
+gets) is copied to the host and written as DIR/<name>.npy, see dump_outputs().
+The inputs come from the seeded generator, so two builds run with the same
+arguments decode the same bytes.
+
+--full adds everything else (none of it feeds `value`): the headline
+column's validation, R = --repeats further regions of K steps for the
+spread, per-kernel HIP-event times and the roofline, the strong-scaling
+figure (N > 1), C3 regex page filter (configs[2]) and PLAIN decode, C4 8
+mixed columns, C5 dictionary decode + regex, end-to-end (host walk + H2D +
+decode), the wide-dictionary and codec legs, CPU baselines (each with its
+own --no-* switch).  Every leg's result is checked against the generator's
+own value dump (pinned to the oracle by the CPU tests) or the committed
+regex page-set digests (tests/golden/bench_expect.json).  The full record
+of a --full run goes to --full-json.
 
 Rank 0 prints ONE JSON line (contract in the task statement).
 """
@@ -53,6 +68,7 @@ KERNELS = ("dict_index", "dict_entries", "pipe_runs", "pipe_big", "wide_chars", 
            "ba_fused", "ba_rows", "scan", "ba_gather", "plain_spec", "plain_ba", "fixed_plain", "fixed", "plain_opt")
 REGEX_KERNELS = ("regex_dict", "regex_codes", "regex_lanes", "regex_plain", "regex_pages")
 ROWS = 10_000_000
+SETTLE_S = 0.25  # untimed decode steps that end the headline's set-up (clock ramp), see c2_leg
 C3_PATTERNS = ("special.*requests", "^(carefully|quickly) ", "[0-9]", "e")
 C5_PATTERN = "^qx"  # splits C5's pages (≈7% reported): not an all-miss scan
 
@@ -62,7 +78,14 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--repeats", type=int, default=5, help="timed regions of --steps steps (median reported)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every other leg and check (validation, spread, per-kernel times and roofline, "
+                         "C3/C4/C5, end to end, wide dictionary, codecs, CPU baselines); off: the headline steps only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step decoded as DIR/<name>.npy (see dump_outputs)")
+    ap.add_argument("--repeats", type=int, default=5,
+                    help="--full: further timed regions of --steps steps after the headline region (spread; "
+                         "the legs report their median)")
     ap.add_argument("--rows", type=int, default=ROWS, help="C2 rows per GPU")
     ap.add_argument("--layout", choices=["ref", "arrow"], default="ref")
     ap.add_argument("--no-regex", action="store_true")
@@ -151,11 +174,11 @@ class Job:
         self.dist.all_gather_object(out, obj)
         return out
 
-    def timed(self, step, check, steps, repeats, warmup=0, kernels=KERNELS):
+    def timed(self, step, check, steps, repeats, warmup=0, kernels=KERNELS, profile=True):
         """`repeats` regions of exactly `steps` steps, each bracketed by a
-        barrier + sync; seconds per region (max over ranks), then the same
-        steps once more with per-kernel HIP events (events perturb the wall
-        clock, so they stay outside the timed regions)."""
+        barrier + sync; seconds per region (max over ranks), then (`profile`)
+        the same steps once more with per-kernel HIP events (events perturb
+        the wall clock, so they stay outside the timed regions)."""
         import torch
         for _ in range(warmup):
             step()
@@ -174,6 +197,8 @@ class Job:
             secs.append(t1 - t0)
         check()
         secs = self.max_all(secs)
+        if not profile:
+            return secs, {}
         self.ctx.timing(True)
         self.ctx.timing_reset()
         for _ in range(steps):
@@ -258,6 +283,55 @@ def pmc_step_traffic(path: str, kern: dict):
 
 def sha(b: bytes) -> str:
     return hashlib.sha256(b).hexdigest()
+
+
+DUMP_SEED = 20240229
+DUMP_ROWS = 1 << 20   # sampled rows (validity, offsets)
+DUMP_CHARS = 1 << 22  # sampled char positions
+DUMP_BLOCK = 4096
+
+
+def _block_sums(a):
+    """float64 sums of consecutive DUMP_BLOCK-element blocks (exact: every
+    sum is an integer far below 2^53), so no element is left unchecked."""
+    import numpy as np
+    a = np.asarray(a)
+    pad = (-len(a)) % DUMP_BLOCK
+    if pad:
+        a = np.concatenate([a, np.zeros(pad, a.dtype)])
+    return a.reshape(-1, DUMP_BLOCK).sum(axis=1, dtype=np.int64).astype(np.float64)
+
+
+def dump_outputs(host, outdir: str, rank: int, world: int) -> None:
+    """The decoded column of the last timed step (what the decode hands its
+    caller: validity, offsets, chars) as <name>.npy (<name>.rank<r>.npy with
+    more than one rank), about 29 MB at the default size:
+      validity.npy  float32  0/1 of the sampled rows
+      offsets.npy   float64  offsets of the sampled rows, then offsets[-1]
+      chars.npy     float32  the chars at the sampled positions
+      {validity,offsets,chars}_sums.npy  float64  block sums of the WHOLE array
+    The samples are fixed: sorted draws of a generator seeded with DUMP_SEED
+    over [0, rows) and [0, chars); an array no longer than its sample size is
+    written whole."""
+    import numpy as np
+    os.makedirs(outdir, exist_ok=True)
+    rng = np.random.default_rng(DUMP_SEED)
+    n = host.num_rows
+    rows = np.sort(rng.integers(0, n, DUMP_ROWS)) if n > DUMP_ROWS else np.arange(n)
+    nchars = len(host.data)
+    pos = np.sort(rng.integers(0, nchars, DUMP_CHARS)) if nchars > DUMP_CHARS else np.arange(nchars)
+    arrays = {"validity": host.validity[rows].astype(np.float32),
+              "validity_sums": _block_sums(host.validity),
+              "chars": host.data[pos].astype(np.float32),
+              "chars_sums": _block_sums(host.data)}
+    if host.offsets is not None:
+        arrays["offsets"] = np.concatenate([host.offsets[rows], host.offsets[-1:]]).astype(np.float64)
+        arrays["offsets_sums"] = _block_sums(host.offsets)
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= 64 << 20, f"--dump-outputs would write {total} bytes"
+    suffix = f".rank{rank}" if world > 1 else ""
+    for name, a in arrays.items():
+        np.save(os.path.join(outdir, f"{name}{suffix}.npy"), a)
 
 
 def expectations():
@@ -437,24 +511,42 @@ def c2_leg(J, args, exp):
     upload_s = time.perf_counter() - t0
     dc.decode()
     nrows = dc.num_rows
-    host = dc.to_host()
-    nonnull = int(host.validity.sum())
-    chars = int(dc.out.num_bytes)
+    nonnull = chars = None
     valid = None
     want = None
-    if not args.no_validate:
-        # this rank's row group against the generator's dump of it
-        want = sha(gen.values_dump(gen.c2_cols()[0], 0, args.rows, J.rank, gen.CONFIG_SEEDS["C2"]))
-        ok = sha(capi.canonical_dump(host)) == want
-        valid = all(J.gather(bool(ok)))
-    del host
-    secs, kern = J.timed(dc.decode_async, dc.decode_check, args.steps, args.repeats, warmup=args.warmup)
+    if args.full:
+        host = dc.to_host()
+        nonnull = int(host.validity.sum())
+        chars = int(dc.out.num_bytes)
+        if not args.no_validate:
+            # this rank's row group against the generator's dump of it
+            want = sha(gen.values_dump(gen.c2_cols()[0], 0, args.rows, J.rank, gen.CONFIG_SEEDS["C2"]))
+            ok = sha(capi.canonical_dump(host)) == want
+            valid = all(J.gather(bool(ok)))
+        del host
+    # set-up ends with the GPU at its running clocks: generation and upload
+    # above left it idle, and the one timed region below has no later regions
+    # to take a median over (SETTLE_S of untimed steps, before the warmup)
+    t0 = time.perf_counter()
+    while time.perf_counter() - t0 < SETTLE_S:
+        dc.decode_async()
+        dc.decode_check()
+    # the headline: W warmup steps, then one region of exactly --steps steps
+    secs, _ = J.timed(dc.decode_async, dc.decode_check, args.steps, 1, warmup=args.warmup, profile=False)
+    if args.dump_outputs:
+        dump_outputs(dc.to_host(), args.dump_outputs, J.rank, J.world)
+    spread, kern = [], {}
+    if args.full:
+        spread, kern = J.timed(dc.decode_async, dc.decode_check, args.steps, args.repeats)
     rows_all = J.sum_all([nrows])[0]
-    med = statistics.median(secs)
-    res = {"secs": secs, "median_s": med, "value": rows_all * args.steps / med, "nrows": nrows,
+    med = secs[0]
+    res = {"secs": secs, "spread_secs": spread, "median_s": med, "value": rows_all * args.steps / med, "nrows": nrows,
            "rows_all": rows_all, "nonnull": nonnull, "chars": chars, "payload": dc.payload_bytes,
            "pages": dc.num_pages, "kern": kern, "validated": valid, "row_group": J.rank,
            "gen_s": gen_s}
+    if not args.full:
+        dc.free()
+        return res
     if not args.no_e2e and J.rank == 0:
         # end to end from host file bytes: host page walk + image build + H2D
         # (+ allocation) + one decode, each the median of 3 (reported
@@ -1119,7 +1211,7 @@ def main():
         print(json.dumps(cpu_baselines(args)), flush=True)
         return
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu:
         # in a fresh child interpreter, started before this process touches
         # the GPU (its own process pool forks; nothing GPU-side is shared)
         r = subprocess.run([sys.executable, os.path.abspath(__file__), "--cpu-only"] + sys.argv[1:],
@@ -1145,21 +1237,6 @@ def main():
     nrows = c2["nrows"]
     med = c2["median_s"]
     ms_per_step = med / args.steps * 1e3
-    kern = {k: v["ms_per_launch"] for k, v in c2["kern"].items()}
-    total_chars = c2["chars"]
-    payload = c2["payload"]
-    out_bytes = 8 * (nrows + 1) + total_chars + (nrows + 7) // 8
-    b_alg = payload + out_bytes  # SURVEY §8d C2 algorithmic bytes per decode
-    dom = max(kern, key=kern.get) if kern else "pipe_write"
-    dom_ms = kern.get(dom, ms_per_step)
-    # algorithmic bytes of one launch of the dominant kernel (DESIGN.md §4):
-    # pipe_write produces the decoded column (offsets, chars, validity); the
-    # u16 codes it reads are this design's intermediate, not algorithmic bytes
-    dom_bytes = {"pipe_write": out_bytes, "pipe_codes": payload,
-                 "ba_fused": b_alg}.get(dom, payload)
-    achieved = dom_bytes / (dom_ms * 1e-3) / 1e9
-    traffic, tsrc = pmc_traffic(args.pmc_json, dom)
-    step_traffic = pmc_step_traffic(args.pmc_json, c2["kern"])
 
     result = {
         "metric": "decoded values/sec (RLE+dict BYTE_ARRAY) and regex pages/sec at 1/2/4/8 GPUs",
@@ -1178,23 +1255,50 @@ def main():
                                f"{args.rows * world}-row column), {args.layout}-layout, 1000-entry dict, 5% NULL",
                    "rows_per_gpu": nrows, "pages_per_gpu": c2["pages"],
                    "parallelism": f"row-group shards x{world} (no collective)"},
-        "timing": {"repeats_ms_per_step": [s / args.steps * 1e3 for s in c2["secs"]],
-                   "statistic": f"median of {args.repeats} regions of {args.steps} steps, max over ranks"},
+        "timing": {"statistic": f"one region of {args.steps} steps after {args.warmup} warmup steps, max over ranks",
+                   "settle_s": SETTLE_S},
         "validated": c2["validated"],
-        "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                     "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": tsrc,
-                     "kernel": dom, "kernel_ms": dom_ms, "algorithmic_bytes": dom_bytes,
-                     "step_traffic": step_traffic["bytes"] if step_traffic else None,
-                     "step_traffic_over_b_alg": step_traffic["bytes"] / b_alg if step_traffic else None,
-                     "step_traffic_per_kernel": step_traffic["per_kernel"] if step_traffic else None},
-        "pipeline": {"kernel_ms": kern,
-                     "kernel_ms_note": "HIP events on the decode streams, same steps repeated after the timed "
-                                       "regions (events perturb the wall clock)",
-                     "sum_kernel_ms": sum(kern.values()),
-                     "b_alg_bytes": b_alg, "b_alg_GBs_per_step": b_alg / (ms_per_step * 1e-3) / 1e9,
-                     "b_alg_frac_of_peak": b_alg / (ms_per_step * 1e-3) / 1e9 / HBM_PEAK_GBS,
-                     "nonnull": c2["nonnull"], "chars": total_chars},
     }
+    if args.dump_outputs:
+        result["outputs"] = args.dump_outputs
+    if not args.full:
+        ctx.close()
+        if rank == 0:
+            print(json.dumps(result), flush=True)
+        if dist is not None:
+            dist.destroy_process_group()
+        return
+
+    result["timing"]["spread_ms_per_step"] = [s / args.steps * 1e3 for s in c2["spread_secs"]]
+    result["timing"]["spread_note"] = f"{args.repeats} further regions of {args.steps} steps after the headline region"
+    kern = {k: v["ms_per_launch"] for k, v in c2["kern"].items()}
+    total_chars = c2["chars"]
+    payload = c2["payload"]
+    out_bytes = 8 * (nrows + 1) + total_chars + (nrows + 7) // 8
+    b_alg = payload + out_bytes  # SURVEY §8d C2 algorithmic bytes per decode
+    dom = max(kern, key=kern.get) if kern else "pipe_write"
+    dom_ms = kern.get(dom, ms_per_step)
+    # algorithmic bytes of one launch of the dominant kernel (DESIGN.md §4):
+    # pipe_write produces the decoded column (offsets, chars, validity); the
+    # u16 codes it reads are this design's intermediate, not algorithmic bytes
+    dom_bytes = {"pipe_write": out_bytes, "pipe_codes": payload,
+                 "ba_fused": b_alg}.get(dom, payload)
+    achieved = dom_bytes / (dom_ms * 1e-3) / 1e9
+    traffic, tsrc = pmc_traffic(args.pmc_json, dom)
+    step_traffic = pmc_step_traffic(args.pmc_json, c2["kern"])
+    result["roofline"] = {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                          "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": tsrc,
+                          "kernel": dom, "kernel_ms": dom_ms, "algorithmic_bytes": dom_bytes,
+                          "step_traffic": step_traffic["bytes"] if step_traffic else None,
+                          "step_traffic_over_b_alg": step_traffic["bytes"] / b_alg if step_traffic else None,
+                          "step_traffic_per_kernel": step_traffic["per_kernel"] if step_traffic else None}
+    result["pipeline"] = {"kernel_ms": kern,
+                          "kernel_ms_note": "HIP events on the decode streams, same steps repeated after the timed "
+                                            "regions (events perturb the wall clock)",
+                          "sum_kernel_ms": sum(kern.values()),
+                          "b_alg_bytes": b_alg, "b_alg_GBs_per_step": b_alg / (ms_per_step * 1e-3) / 1e9,
+                          "b_alg_frac_of_peak": b_alg / (ms_per_step * 1e-3) / 1e9 / HBM_PEAK_GBS,
+                          "nonnull": c2["nonnull"], "chars": total_chars}
     if "e2e" in c2:
         result["end_to_end"] = {"c2": c2["e2e"]}
     if "api_read_all" in c2:

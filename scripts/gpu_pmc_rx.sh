@@ -10,7 +10,7 @@ cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 OUT=gpurun_out/$TAG
 mkdir -p "$OUT"
 export TMPDIR=/tmp
-C2_ARGS="--no-cpu --no-c4 --no-c5 --no-ext --no-wide --no-e2e --steps 10 --warmup 2 --repeats 1"
+C2_ARGS="--full --no-cpu --no-c4 --no-c5 --no-ext --no-wide --no-e2e --steps 10 --warmup 2 --repeats 1"
 timeout -k 10 300 rocprofv3 --kernel-trace --stats -T -d "$OUT/prof_kt" -o kt --output-format csv -- \
     python3 bench.py $C2_ARGS "$@" > "$OUT/prof_kt.log" 2>&1
 rc=$?; [ $rc -eq 0 ] || { echo "KT rc=$rc"; tail -20 "$OUT/prof_kt.log"; exit $rc; }

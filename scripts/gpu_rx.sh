@@ -12,7 +12,7 @@ timeout -k 10 600 python -u -m pytest tests/test_gpu_regex.py tests/test_gpu_c3_
 rc=$?; tail -3 "$OUT/pytest.log"; [ $rc -eq 0 ] || { grep -E "Error|assert" "$OUT/pytest.log" | head -20; exit $rc; }
 timeout -k 10 240 python3 scripts/regex_ablate.py > "$OUT/regex_ablate.txt" 2>&1
 rc=$?; cat "$OUT/regex_ablate.txt"; [ $rc -eq 0 ] || exit $rc
-timeout -k 10 300 python bench.py --no-cpu --no-c4 --no-c5 --no-ext --no-wide --no-e2e --steps 10 > "$OUT/rx.json" 2> "$OUT/rx.err"
+timeout -k 10 300 python bench.py --full --no-cpu --no-c4 --no-c5 --no-ext --no-wide --no-e2e --steps 10 > "$OUT/rx.json" 2> "$OUT/rx.err"
 rc=$?; [ $rc -eq 0 ] || { tail -5 "$OUT/rx.err"; exit $rc; }
 python3 - "$OUT/rx.json" <<'PY'
 import json, sys
