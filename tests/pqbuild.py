@@ -93,6 +93,29 @@ def data_header(size: int, nvals: int, enc: int = 0, ptype: int = 0, with_dph: b
     return bytes(t.stop().b)
 
 
+def data_header_v2(size: int, nvals: int, usize: int, def_len: int = 0, rep_len: int = 0, enc: int = 0,
+                   num_nulls: int = 0, is_compressed: bool | None = None) -> bytes:
+    """A DATA_PAGE_V2 header (page type 3, DataPageHeaderV2 in field 8): `size`
+    and `usize` count the level sections (stored as is) plus the values as
+    stored / uncompressed.  is_compressed None leaves the field out (the
+    format's default is true)."""
+    t = TW().i32(1, 3).i32(2, usize).i32(3, size)
+    t.begin(8).i32(1, nvals).i32(2, num_nulls).i32(3, nvals).i32(4, enc).i32(5, def_len).i32(6, rep_len)
+    if is_compressed is not None:
+        t.field(7, 1 if is_compressed else 2)
+    t.end()
+    return bytes(t.stop().b)
+
+
+def carrier(length: int) -> tuple[int, int]:
+    """(physical type, values per page) of the REQUIRED PLAIN column that
+    carries `length` payload bytes as they are: INT32 (type 1) when the length
+    is a multiple of 4, the decoded data then equals the payload; otherwise
+    BOOLEAN (type 0) with 8 values per byte, one decoded byte per bit
+    (np.unpackbits(payload, bitorder="little"))."""
+    return (1, length // 4) if length % 4 == 0 else (0, 8 * length)
+
+
 def dict_header(size: int, nvals: int) -> bytes:
     return bytes(TW().i32(1, 2).i32(2, size).i32(3, size).begin(7).i32(1, nvals).i32(2, 2).end().stop().b)
 
@@ -121,15 +144,17 @@ def plain_ba(values) -> bytes:
 
 def build_file(pages: list[bytes], ptype: int, optional: bool, num_values: int,
                dict_at_start: bool = False, name: bytes = b"c", pad_footer: bool = True, codec: int = 0,
-               nested: str | None = None):
+               nested: str | None = None, lead: bytes = b""):
     """pages: list of (header + payload) blobs laid out back to back.
+    lead: junk bytes between PAR1 and the first page (moves every payload's
+    address mod 16).
     nested: None (one flat leaf: max_def = optional, max_rep 0), "repeated"
     (a REPEATED leaf: max_def 1, max_rep 1) or "list" (the LIST shape
     optional group a / repeated group list / leaf element: max_def 2 +
     optional, max_rep 1), levels as ParquetReader::build_columns_recursive
     counts them (parquet_reader.cpp:495-543).
     Returns (file bytes, chunk dict for the oracle/C ABI)."""
-    body = b"PAR1"
+    body = b"PAR1" + lead
     start = len(body)
     for p in pages:
         body += p
