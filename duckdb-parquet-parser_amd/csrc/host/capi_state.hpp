@@ -1,6 +1,8 @@
 // capi_state.hpp — the C ABI's context and device-chunk state (pq_ctx,
-// pq_chunk) and the planning functions that size a chunk's launches
-// (host/plan.cpp), shared by capi.hip (entry points, uploads, launches).
+// pq_chunk), the image's slot layout (slot_bytes), what the stages of an
+// upload share (UploadPlan) and the planning functions that size a chunk's
+// launches (host/plan.cpp).  Shared by plan.cpp and the capi*.hip files
+// (capi.hip: contexts; capi_upload.hip; capi_decode.hip; capi_regex.hip).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -91,7 +93,7 @@ struct pq_ctx {
     std::vector<PendingTimer> pending;
     std::vector<std::pair<hipEvent_t, hipEvent_t>> free_events;
     std::map<std::string, std::pair<double, int64_t>> timers;
-    // upload scratch (upload_walked): per-page host tables, reused
+    // upload scratch (UploadPlan): per-page host tables, reused
     PVec<pqk::DevPage> s_hpages;
     HVec<std::pair<int64_t, int64_t>> s_copies;
     HVec<int32_t> s_copy_size;
@@ -283,7 +285,8 @@ struct pq_chunk {
     pqre::DeviceProgram* d_prog = nullptr;
 };
 
-namespace pqcapi {
+// (internal to libpqgpu.so: what these headers declare is not exported)
+namespace pqcapi __attribute__((visibility("hidden"))) {
 
 template <class T>
 int dalloc(T** p, size_t n) {
@@ -296,15 +299,58 @@ void dfree(T*& p) {
     if (p) (void)hipFree(p);
     p = nullptr;
 }
+// A buffer the context keeps across calls, grown to `need` elements (its
+// contents dropped).  False: hipMalloc failed and the buffer is gone.
+template <class T>
+bool dgrow(T*& p, size_t& cap, size_t need) {
+    if (cap >= need) return true;
+    dfree(p);
+    cap = 0;
+    if (dalloc(&p, need)) return false;
+    cap = need;
+    return true;
+}
+
+// Bytes of a payload's slot in the device image: 16-byte aligned, plus 16
+// bytes that every kernel's over-read relies on (the kernels keep their own
+// copies of this formula).
+inline int64_t slot_bytes(int64_t payload) { return (payload + 15) / 16 * 16 + 16; }
+
+// A dictionary page of `size` bytes holds at most size / 4 + 1 BYTE_ARRAY
+// entries: a corrupt header count must not size a table.
+inline int64_t dict_entry_cap(int64_t nvals, int64_t size) { return std::min<int64_t>(nvals, size / 4 + 1); }
+
+// What the stages of one upload share (capi_upload.hip upload_walked).  The
+// per-page tables are the context's scratch: capacity kept across uploads, so
+// a reader walking many row groups does not page-fault fresh tables in each
+// time (a context serves one thread at a time).
+struct UploadPlan {
+    PVec<DevPage>& hpages;
+    HVec<std::pair<int64_t, int64_t>>& copies;  // (file offset, image offset) per payload; -1: a codec page
+    HVec<int32_t>& copy_size;
+    PVec<DevTile>& htiles;
+    PVec<int32_t>& tile0;
+    PVec<pqk::RelayoutEntry>& ents;
+    std::vector<DevDict> hdicts;
+    // pages the codec pass rebuilds (compressed or DATA_PAGE_V2): their slot
+    // holds the V1-layout payload; the image build leaves it zero
+    std::vector<pqk::CodecEntry> cents;
+    std::vector<int64_t> cent_file;  // payload file offset per codec entry
+    int64_t seq = 0, row_base = 0, img = 0;  // walk sequence, rows and image bytes so far
+    explicit UploadPlan(pq_ctx* ctx)
+        : hpages(ctx->s_hpages), copies(ctx->s_copies), copy_size(ctx->s_copy_size), htiles(ctx->s_htiles),
+          tile0(ctx->s_tile0), ents(ctx->s_ents) {}
+};
 
 // host/plan.cpp
 void plan_pipe(pq_ctx* ctx, pq_chunk* c, const PVec<DevPage>& pages, const std::vector<DevDict>& dicts);
 void plan_plain(pq_ctx* ctx, pq_chunk* c, const PVec<DevPage>& pages);
 void plan_fused(pq_ctx* ctx, pq_chunk* c, const PVec<DevPage>& pages, const std::vector<DevDict>& dicts);
 bool plan_pages_parallel(pq_chunk* c, const pq_chunk_desc& desc, const pqfmt::WalkResult& w, bool keep_walk, int hw,
-                         int64_t seq, int64_t& row_base, int64_t& img, PVec<DevPage>& hpages,
-                         std::vector<DevDict>& hdicts, HVec<std::pair<int64_t, int64_t>>& copies,
-                         HVec<int32_t>& copy_size);
+                         UploadPlan& up);
+void plan_pages_serial(pq_chunk* c, const pq_chunk_desc& desc, const pqfmt::WalkResult& w, bool keep_walk,
+                       size_t file_len, UploadPlan& up);
+void plan_tiles(pq_chunk* c, int hw, UploadPlan& up);
 bool plan_regex_windows(pq_ctx* ctx, pq_chunk* c);
 
 }  // namespace pqcapi

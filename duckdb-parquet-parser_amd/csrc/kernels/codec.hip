@@ -4,7 +4,7 @@
 //
 // Each entry turns one page payload, as the file holds it (raw chunk bytes in
 // HBM), into the payload the decode kernels read, written to the page's slot
-// in the chunk image (capi.hip `slot`):
+// in the chunk image (host/capi_state.hpp slot_bytes):
 //   V1 page, codec C:  decompress(payload)
 //   V2 page:           [u32 def_len][def levels] (max_def > 0)
 //                      [u32 rep_len][rep levels] (max_rep > 0)

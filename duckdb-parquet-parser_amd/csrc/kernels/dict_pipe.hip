@@ -563,8 +563,8 @@ __device__ __forceinline__ uint32_t wave_shr1(uint32_t v) {  // lane i <- lane i
 //    the next tile, before that tile's prefetch (one wait per tile, for
 //    operations issued a whole tile earlier);
 //  * bit fields come from the staged payload without branches: two clamped
-//    dword reads and a funnel shift (the slot's zero padding, capi.hip
-//    `slot`, stands for the bytes past the page end);
+//    dword reads and a funnel shift (the slot's zero padding, host/capi_state.hpp
+//    slot_bytes, stands for the bytes past the page end);
 //  * every row takes the same instructions (selects, not branches).
 // Pages whose payload does not fit the stage (> kStage3 - 16 bytes), and every
 // page when the dictionary has more entries than the LDS length table, take
@@ -1619,7 +1619,7 @@ struct BigLayout {  // dynamic LDS of k_pipe_big for a page of `size` payload by
 };
 __host__ __device__ inline BigLayout big_layout(uint32_t size, uint32_t nlens) {
     BigLayout L{};
-    L.P = (size + 16 + 15) / 16 * 16;            // = the payload slot (capi.hip)
+    L.P = (size + 16 + 15) / 16 * 16;            // = the payload slot (host/capi_state.hpp slot_bytes)
     // the jump table covers the page in one segment, or (pages over
     // kBigSegBytes) in two halves one after the other
     L.nseg = size > kBigOneSeg ? 2u : 1u;
@@ -2416,7 +2416,7 @@ void launch_pipe_runs(hipStream_t s, const uint8_t* bytes, const DevPage* pages,
                       int32_t max_rep, uint2* runs, uint32_t* info, int pages_per_wave, int32_t* flist,
                       int debug, const RunDicts* dicts, uint32_t stage_max, uint32_t slot_max, uint32_t dict_max,
                       int cus) {
-    (void)flist;  // flist[0] is cleared by the caller (capi.hip: one memset of flags, bsum, flist[0])
+    (void)flist;  // flist[0] is cleared by the caller (capi_decode.hip decode_launch: one memset of flags, bsum, flist[0])
     const int nd = dicts ? dicts->ndicts : 0;
     if (npages <= 0 && nd <= 0) return;
     int ppw = pages_per_wave > 0 && pages_per_wave <= kRunPages ? pages_per_wave : kRunPages;

@@ -1,5 +1,5 @@
 // kernels.hpp — device-side data layout shared by the HIP kernels and the
-// C-ABI host code (capi.hip).  See DESIGN.md "Data layout in HBM".
+// C-ABI host code (capi*.hip, host/plan.cpp).  See DESIGN.md "Data layout in HBM".
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -88,7 +88,7 @@ __device__ int lane_rle(LRle& r, Rd8&& rd8, uint32_t need, F&& emit) {
 }
 
 // 8 bytes at page byte a of a 16-byte aligned page slot in global memory
-// (slots carry >= 16 zero bytes after the payload, capi.hip).
+// (slots carry >= 16 zero bytes after the payload, host/capi_state.hpp slot_bytes).
 __device__ __forceinline__ uint64_t gld8(const uint8_t* page, uint32_t a) {
     const uint32_t* w = reinterpret_cast<const uint32_t*>(page) + (a >> 2);
     const uint32_t d0 = w[0], d1 = w[1], d2 = w[2], sh = a & 3;

@@ -7,7 +7,7 @@
 // compiler use SMEM (s_load_dword*) with the cursor in SGPRs: one scalar
 // load and a handful of SALU ops per run header, no vector memory round trip
 // and no vmcnt waits on the critical path.  Payloads sit 16-byte aligned in
-// the device image with at least 16 zero bytes after them (capi.hip), so the
+// the device image with at least 16 zero bytes after them (host/capi_state.hpp slot_bytes), so the
 // 12-byte scalar reads never leave the allocation.
 //
 // RLE runs are expanded into LDS immediately (stores only, nothing waits on

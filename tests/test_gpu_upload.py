@@ -11,8 +11,8 @@ import numpy as np
 import pytest
 
 from pqgpu import capi, gen
-from pqgpu.shard import data_page_ranges
-from util import oracle_read_column
+from pqgpu.shard import data_page_ranges, extract_range
+from util import file_chunks, gpu_read_column, oracle_read_column
 
 pytestmark = pytest.mark.gpu
 
@@ -120,3 +120,50 @@ def test_page_range_raw_upload(ctx):
             dc.free()
         ctx.set_option("raw_upload", 1)
         assert b"".join(parts) == exp
+
+
+def test_many_small_pages_threaded_plan(ctx):
+    """37,500 data pages per chunk: enough for the threaded page, tile, window
+    and relayout planners to cut their work into more than one range (one per
+    16,384 pages of a walk), which no other default test reaches."""
+    cols = [
+        gen.Col("s", gen.DICT_STRINGS, gen.BYTE_ARRAY, optional=True, null_frac=0.1,
+                dict_size=500, len_min=2, len_max=9, max_run=4),
+        gen.c4_cols()[0],
+    ]
+    f = gen.build(cols, 300_000, 2, seed=5, layout=gen.ARROW_LAYOUT, rows_per_page=8)
+    for col in range(len(cols)):
+        chunks = file_chunks(f, col)
+        exp = oracle_read_column(f, chunks)
+        assert exp[0] == 0, exp[1]
+        for raw in (1, 0):
+            ctx.set_option("raw_upload", raw)
+            try:
+                assert gpu_read_column(ctx, f, chunks) == exp, (col, raw)
+            finally:
+                ctx.set_option("raw_upload", 1)
+    # a middle page range of column 0's first chunk: the matching slice of the chunk
+    ch = file_chunks(f, 0)[0]
+    rc, msg, table = capi.build_page_table(f, ch)
+    assert rc == 0 and sum(p.page_type == 0 for p in table) == 37_500
+    a, b = data_page_ranges(table, 3)[1]
+    assert 0 < a < b < 37_500
+
+    def oracle_range(lo, hi):
+        sub, desc = extract_range(f, ch, table, lo, hi)
+        rc, msg, out = oracle_read_column(sub, [desc])
+        assert rc == 0, msg
+        return out
+
+    head, want = oracle_range(0, a), oracle_range(a, b)
+    assert oracle_read_column(f, [ch])[2][len(head):len(head) + len(want)] == want
+    for raw in (1, 0):
+        ctx.set_option("raw_upload", raw)
+        try:
+            dc = ctx.upload_range(f, ch, table, a, b)
+            dc.decode()
+            got = capi.canonical_dump(dc.to_host())
+            dc.free()
+        finally:
+            ctx.set_option("raw_upload", 1)
+        assert got == want, raw
