@@ -662,6 +662,15 @@ extern "C" int pq_regex_dfa_info(const char* pattern, int* nstates, int* nclasse
     return 0;
 }
 
+// Whether the pattern's matches start at byte 0 only (first_mid == 0: with a
+// full table the windowed scan takes its kSink form).  1/0, or PQ_ERR_REGEX.
+extern "C" int pq_regex_anchored(const char* pattern) {
+    pqre::Program p;
+    std::string msg;
+    if (pqre::compile(pattern ? pattern : "", &p, &msg)) return PQ_ERR_REGEX;
+    return p.first_mid == 0 ? 1 : 0;
+}
+
 // The DFA's absorbing-state masks (test hook; k_regex_plain<true> stops a
 // batch once every string sits in one).  PQ_ERR_REGEX / PQ_ERR_UNSUPPORTED
 // as above.

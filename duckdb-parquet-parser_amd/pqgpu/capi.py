@@ -126,6 +126,8 @@ def lib():
             "pq_regex_pages_result": ([vp, vp, vp], C.c_int),
             "pq_regex_match_host": ([C.c_char_p, u8p, C.c_size_t], C.c_int),
             "pq_regex_match_host_dfa": ([C.c_char_p, u8p, C.c_size_t], C.c_int),
+            "pq_regex_dfa_info": ([C.c_char_p] + [C.POINTER(C.c_int)] * 4, C.c_int),
+            "pq_regex_anchored": ([C.c_char_p], C.c_int),
             "pq_regex_dfa_sinks": ([C.c_char_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)], C.c_int),
             "pq_timing_enable": ([vp, C.c_int], None),
             "pq_timing_reset": ([vp], None),
@@ -478,6 +480,16 @@ def regex_dfa_sinks(pattern: str):
     lo, hi = C.c_uint32(0), C.c_uint32(0)
     rc = lib().pq_regex_dfa_sinks(pattern.encode(), C.byref(lo), C.byref(hi))
     return rc, (hi.value << 32) | lo.value
+
+
+def regex_dfa_info(pattern: str) -> dict:
+    """The pattern's DFA as the scan kernels get it: rc (0, -22 bad pattern,
+    -8 DFA over its size cap), nstates, nclasses, full (byte-indexed table),
+    bytes (image size) and anchored (matches start at byte 0 only)."""
+    v = [C.c_int(0) for _ in range(4)]
+    rc = lib().pq_regex_dfa_info(pattern.encode(), *[C.byref(x) for x in v])
+    return dict(rc=rc, nstates=v[0].value, nclasses=v[1].value, full=bool(v[2].value), bytes=v[3].value,
+                anchored=lib().pq_regex_anchored(pattern.encode()) == 1)
 
 
 def regex_match_host_dfa(pattern: str, s: bytes) -> int:
